@@ -26,7 +26,15 @@ Multi-GPU (one process per GPU):
   --mode replicas: every rank orders a DAG of its own (weak scaling, no
       data-path collective) -- N copies of the 1-GPU number, labelled so.
 
+A plain run sets up, warms up, times the steps and prints the result line.
+  --full adds what takes a run of its own: the CPU baseline (the oracle on a
+      prefix of the same DAG, `cpu_baseline` / `speedup_vs_cpu` in the line;
+      --cpu-sample sizes it).
+  --dump-outputs DIR writes what the last timed step computed (the arrays of
+      Hashgraph.results(), consensus_order() and blocks()) as DIR/<name>.npy.
+
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg 3] [--events N] [--mode replicas|shards]
+                       [--full] [--dump-outputs DIR]
        torchrun ... bench.py --gpus N ...
 """
 import argparse
@@ -171,6 +179,41 @@ def cpu_baseline(cfg, sample_events, log):
     return out
 
 
+DUMP_SAMPLE = 3 << 18  # per-event / per-position arrays larger than this are sampled (64 B per sample: 50 MB in all)
+
+
+def dump_outputs(hg, out_dir):
+    """What a caller receives after the last timed step, as <name>.npy:
+    results() per event, consensus_order() per position, blocks() per block.
+    Integers go out as float64 (exact: every value is below 2^53), the
+    witness / fame flags as float32.  An array longer than DUMP_SAMPLE is
+    sampled at fixed, seeded, sorted indices (written beside it as
+    sample_events / sample_positions), the same from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def pick(count):
+        if count <= DUMP_SAMPLE:
+            return None
+        return np.sort(np.random.default_rng(0xBABB1E).choice(count, DUMP_SAMPLE, replace=False))
+
+    def save(name, a, idx, dt=np.float64):
+        np.save(os.path.join(out_dir, name + ".npy"), (a if idx is None else a[idx]).astype(dt))
+
+    res = hg.results()
+    idx = pick(len(res["round"]))
+    for k, a in res.items():
+        save(k, a, idx, np.float32 if a.dtype == np.int8 else np.float64)
+    if idx is not None:
+        save("sample_events", idx, None)
+    order = hg.consensus_order()
+    idx = pick(len(order))
+    save("consensus_order", order, idx)
+    if idx is not None:
+        save("sample_positions", idx, None)
+    for k, a in hg.blocks().items():
+        save("block_" + k, a, pick(len(a)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -179,7 +222,12 @@ def main():
     ap.add_argument("--cfg", type=int, default=3)
     ap.add_argument("--events", type=int, default=0, help="override DAG size")
     ap.add_argument("--sig", type=int, default=0, help="1 = deterministic ECDSA signatures")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="events for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=-1,
+                    help="with --full: events for the CPU baseline (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--mode", choices=("shards", "replicas"), default="shards",
                     help="N>1: shard one DAG over the ranks (strong, the default) or order one DAG per rank (weak)")
@@ -395,7 +443,9 @@ def main():
         "round_loop_iterations": iters,
         "pipeline": {"segments": segments, "incremental_calls": hg.pipeline()[1]},
     }
-    cpu_sample = args.cpu_sample
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(hg, args.dump_outputs)
+    cpu_sample = args.cpu_sample if args.full else 0
     if cpu_sample < 0:
         cpu_sample = min(N, {1: 10_000, 2: 1_000_000, 3: 500_000, 4: 100_000, 5: 500_000}[args.cfg])
     if rank == 0 and world == 1 and cpu_sample > 0:

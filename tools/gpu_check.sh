@@ -24,8 +24,8 @@ for s in "$@"; do
     twide) step pytest_wide 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -rf -k "wide or 512 or 300 or c4 or C4 or floww" ;;
     tfloww) step pytest_floww 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -v --timeout 300 --timeout-method thread -rf -x -k "floww" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench2) step bench_c2 600 python bench.py --cfg 2 --steps 3 --warmup 1 ;;
-    bench3) step bench_c3 900 python bench.py --cfg 3 --steps 3 --warmup 1 ;;
+    bench2) step bench_c2 600 python bench.py --full --cfg 2 --steps 3 --warmup 1 ;;
+    bench3) step bench_c3 900 python bench.py --full --cfg 3 --steps 3 --warmup 1 ;;
     serial) step serial 600 env BH_SEG_SERIAL=1 BH_SEG_DEBUG=1 python bench.py --steps 1 --warmup 1 --cpu-sample 0 ;;
     serialrows) step serial_rows 600 env BH_ROUND_ROWS=1 BH_SEG_SERIAL=1 BH_SEG_DEBUG=1 python bench.py --steps 1 --warmup 1 --cpu-sample 0 ;;
     tl) step tl 600 env BH_DIAG=1 BH_TIMELINE=gpurun_out/tl.bin python bench.py --steps 1 --warmup 1 --cpu-sample 0 ;;
@@ -35,7 +35,7 @@ for s in "$@"; do
     bench3qb) step bench_c3b 900 python bench.py --cfg 3 --steps 3 --warmup 1 --cpu-sample 0 ;;
     tlser) step tlser 600 env BH_SEG_SERIAL=1 BH_DIAG=1 BH_TIMELINE=gpurun_out/tlser.bin python bench.py --steps 1 --warmup 1 --cpu-sample 0 ;;
     tlrows) step tlrows 600 env BH_ROUND_ROWS=1 BH_SEG_SERIAL=1 BH_DIAG=1 BH_TIMELINE=gpurun_out/tlrows.bin python bench.py --steps 1 --warmup 1 --cpu-sample 0 ;;
-    bench) step bench 900 python bench.py ;;
+    bench) step bench 900 python bench.py --full ;;
     benchrows) step bench_rows 900 env BH_ROUND_ROWS=1 python bench.py --cpu-sample 0 ;;
     bench4tr32) step bench_c4_tr32 1100 env BH_FDT_TR=32 python bench.py --cfg 4 --steps 1 --warmup 1 --cpu-sample 0 ;;
     bench4x16) step bench_c4_x16 1100 env BH_XPOSE_TR=16 python bench.py --cfg 4 --steps 1 --warmup 1 --cpu-sample 0 ;;
@@ -45,8 +45,8 @@ for s in "$@"; do
     bench3s12) step bench_c3_s12 900 env BH_SEGMENTS=12 python bench.py --cfg 3 --steps 3 --warmup 1 --cpu-sample 0 ;;
     bench3s6) step bench_c3_s6 900 env BH_SEGMENTS=6 python bench.py --cfg 3 --steps 3 --warmup 1 --cpu-sample 0 ;;
     bench3nolt) step bench_c3_nolt 900 env BH_LOOP_TIMING=0 python bench.py --cfg 3 --steps 3 --warmup 1 --cpu-sample 0 ;;
-    bench5) step bench_c5 600 python bench.py --cfg 5 --steps 3 --warmup 1 ;;
-    bench4) step bench_c4 1100 python bench.py --cfg 4 --steps 1 --warmup 1 ;;
+    bench5) step bench_c5 600 python bench.py --full --cfg 5 --steps 3 --warmup 1 ;;
+    bench4) step bench_c4 1100 python bench.py --full --cfg 4 --steps 1 --warmup 1 ;;
     bench4q) step bench_c4 1100 python bench.py --cfg 4 --steps 1 --warmup 1 --cpu-sample 0 ;;
     bench3g0) step bench_c3_g0 900 env BH_ROUND_P8G=0 python bench.py --cfg 3 --steps 3 --warmup 1 --cpu-sample 0 ;;
     bench2g0) step bench_c2_g0 600 env BH_ROUND_P8G=0 python bench.py --cfg 2 --steps 3 --warmup 1 --cpu-sample 0 ;;

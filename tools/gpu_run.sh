@@ -21,7 +21,7 @@ for step in "$@"; do
       IFS=: read -r cfg steps envs <<< "$arg"
       name=${tag}_bench_c${cfg}${envs:+_$(echo $envs | tr ',=' '__')}
       echo "== bench cfg$cfg $envs"
-      cpu=""; [ $kind = benchq ] && cpu="--cpu-sample 0"
+      cpu="--full"; [ $kind = benchq ] && cpu=""
       env $(echo $envs | tr ',' ' ') timeout -k 10 600 python -u bench.py --cfg $cfg --steps $steps --warmup 1 $cpu \
         > $out/$name.json 2> $out/$name.log || { tail -20 $out/$name.log; exit 1; }
       python3 -c "import json,sys; d=json.load(open('$out/$name.json')); print('$name', round(d['value']/1e6,2), 'M ev/s', round(d['ms_per_step'],2), 'ms', d['stages_ms'])" ;;
