@@ -24,8 +24,12 @@ SYMBOLS = (
     "bh_run_consensus", "bh_synchronize", "bh_reset_consensus", "bh_reset", "bh_get_stats", "bh_get_event_meta",
     "bh_get_consensus_order", "bh_get_blocks", "bh_get_pending_rounds", "bh_get_undetermined",
     "bh_get_round_info", "bh_get_coordinates", "bh_query_events", "bh_get_stage_ms", "bh_get_profile", "bh_get_profile_kernel",
-    "bh_get_pipeline", "bh_get_loop_stats", "bh_hash_bodies", "bh_verify_signatures", "bh_set_event_bytes", "bh_get_frame_roots",
-    "bh_get_frame_json", "bh_get_block_hashes", "bh_get_block_json", "bh_comm_unique_id", "bh_comm_init", "bh_comm_init_transport",
+    "bh_get_pipeline", "bh_get_loop_stats", "bh_hash_bodies", "bh_verify_signatures",
+    "bh_set_validators", "bh_verify_fixed", "bh_add_block_signatures", "bh_set_block_signature",
+    "bh_set_reset_block_sign_hash", "bh_process_sig_pool", "bh_get_block_signature_counts", "bh_get_block_signatures",
+    "bh_get_anchor_block", "bh_get_sig_pool", "bh_get_sig_stats", "bh_set_event_bytes", "bh_get_frame_roots",
+    "bh_get_frame_json", "bh_get_block_hashes", "bh_get_block_json",
+    "bh_set_block_state_hashes", "bh_get_block_sign_hashes", "bh_comm_unique_id", "bh_comm_init", "bh_comm_init_transport",
     "bh_shard_range",
 )
 
@@ -70,6 +74,14 @@ class Stats(C.Structure):
                 ("consensus_transactions", C.c_int64), ("pending_loaded_events", C.c_int64),
                 ("undetermined_events", C.c_int64), ("blocks", C.c_int64),
                 ("pending_rounds", C.c_int32), ("first_block", C.c_int64)]
+
+
+class SigStats(C.Structure):
+    _fields_ = [("pool", C.c_int64), ("verified", C.c_int64), ("accepted", C.c_int64),
+                ("verified_total", C.c_int64), ("table_bytes", C.c_int64),
+                ("window_bits", C.c_int32), ("trust_count", C.c_int32),
+                ("verify_signatures_ms", C.c_float), ("verify_fixed_ms", C.c_float),
+                ("set_validators_ms", C.c_float), ("process_sig_pool_ms", C.c_float)]
 
 
 class RoundInfo(C.Structure):
@@ -127,6 +139,28 @@ def load():
     L.bh_hash_bodies.restype = C.c_int
     L.bh_verify_signatures.argtypes = [P, VP, VP, VP, VP, I64, VP, I32, VP]
     L.bh_verify_signatures.restype = C.c_int
+    L.bh_set_validators.argtypes = [P, VP]
+    L.bh_set_validators.restype = C.c_int
+    L.bh_verify_fixed.argtypes = [P, VP, VP, VP, VP, I64, VP]
+    L.bh_verify_fixed.restype = C.c_int
+    L.bh_add_block_signatures.argtypes = [P, I64, VP, VP, VP, VP]
+    L.bh_add_block_signatures.restype = C.c_int
+    L.bh_set_block_signature.argtypes = [P, I64, I32, VP, VP]
+    L.bh_set_block_signature.restype = C.c_int
+    L.bh_set_reset_block_sign_hash.argtypes = [P, VP]
+    L.bh_set_reset_block_sign_hash.restype = C.c_int
+    L.bh_process_sig_pool.argtypes = [P, C.POINTER(I64), C.POINTER(I64)]
+    L.bh_process_sig_pool.restype = C.c_int
+    L.bh_get_block_signature_counts.argtypes = [P, I64, I64, VP]
+    L.bh_get_block_signature_counts.restype = I64
+    L.bh_get_block_signatures.argtypes = [P, I64, VP, VP, VP, I32]
+    L.bh_get_block_signatures.restype = I32
+    L.bh_get_anchor_block.argtypes = [P, C.POINTER(I64)]
+    L.bh_get_anchor_block.restype = C.c_int
+    L.bh_get_sig_pool.argtypes = [P, VP, VP, VP, VP, I64]
+    L.bh_get_sig_pool.restype = I64
+    L.bh_get_sig_stats.argtypes = [P, C.POINTER(SigStats)]
+    L.bh_get_sig_stats.restype = C.c_int
     L.bh_set_event_bytes.argtypes = [P, I64, I64, VP, VP, VP, VP]
     L.bh_set_event_bytes.restype = C.c_int
     L.bh_get_frame_roots.argtypes = [P, I32, VP, VP, VP, VP, VP, I32]
@@ -137,6 +171,10 @@ def load():
     L.bh_get_block_hashes.restype = C.c_int
     L.bh_get_block_json.argtypes = [P, I64, I32, VP, I64]
     L.bh_get_block_json.restype = I64
+    L.bh_set_block_state_hashes.argtypes = [P, I64, I64, VP, VP]
+    L.bh_set_block_state_hashes.restype = C.c_int
+    L.bh_get_block_sign_hashes.argtypes = [P, I64, I64, VP, VP]
+    L.bh_get_block_sign_hashes.restype = C.c_int
     L.bh_comm_unique_id.argtypes = [VP]
     L.bh_comm_unique_id.restype = C.c_int
     L.bh_comm_init.argtypes = [P, I32, I32, VP]

@@ -49,6 +49,7 @@ void free_all(bh_handle *h) {
   if (h->pinned_state) (void)hipHostFree(h->pinned_state);
   if (h->pin_rd) (void)hipHostFree(h->pin_rd);
   if (h->sha_buf) (void)hipFree(h->sha_buf);
+  sig_free(h);
   if (h->q_buf) (void)hipFree(h->q_buf);
   if (h->pack_buf) (void)hipFree(h->pack_buf);
   if (h->graph) (void)hipGraphExecDestroy(h->graph);
@@ -2483,6 +2484,7 @@ int bh_reset_consensus(bh_handle *h) {
     x->inc_valid = false;
     x->n_coord = 0;
     if (x->frames_on) frames_reset(x);
+    sig_pool_forget(x);
   }
   HIPCHK(h, hipSetDevice(h->device));
   return BH_OK;
@@ -3198,10 +3200,15 @@ int bh_verify_signatures(bh_handle *h, const uint8_t *hashes, const uint8_t *sig
   HIPCHK(h, hipMemcpyAsync(ds, sig_s, (size_t)count * 32, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dk, keys, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dp, pubkeys, (size_t)n_keys * 64, hipMemcpyHostToDevice, h->stream));
+  // (timed only on a handle whose validators are set: bh_get_sig_stats)
+  const bool timed = h->sig_window != 0;
+  if (timed) HIPCHK(h, hipEventRecord(h->ev_sig[0], h->stream));
   bh::launch_ecdsa_verify(dh, dr, ds, dk, dp, count, dok, h->stream);
   HIPCHK(h, hipGetLastError());
+  if (timed) HIPCHK(h, hipEventRecord(h->ev_sig[1], h->stream));
   HIPCHK(h, hipMemcpyAsync(ok, dok, (size_t)count, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, wait_stream(h->stream));
+  if (timed) HIPCHK(h, hipEventElapsedTime(&h->verify_ms, h->ev_sig[0], h->ev_sig[1]));
   return BH_OK;
 }
 

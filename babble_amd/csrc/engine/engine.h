@@ -282,6 +282,16 @@ struct Frames {
   int8_t *fvalid;                // [R1] fhash / bhash computed
   uint8_t *dig;                  // [R1][32] scratch digests
   uint8_t *json, *bjson;         // materialized Frame / Block JSON of the last projection
+  // What validators sign (Block.Sign / Verify, block.go:215-254): SHA-256
+  // of BlockBody.Marshal() (block.go:21-46), with the StateHash the app's
+  // CommitBlock gave (node.go:619; bh_set_block_state_hashes)
+  uint8_t *shash;                // [R1][32] sign hash of frame f's block
+  int32_t *st_len;               // [R1] Body.StateHash length, -1 = nil ("StateHash":null)
+  uint8_t *st_bytes;             // [R1][64] Body.StateHash
+  int32_t *bver;                 // [R1] bumped whenever the block's body changes
+  int64_t *sofs;                 // [R1] scratch: the body's span within bjson
+  int32_t *slen;
+  uint8_t *sdig;                 // [R1][32] scratch digests
   // A Reset hashgraph's installed Roots (bh_reset with frames; null
   // otherwise): a participant with no consensus event since the Reset keeps
   // its Root whole in every frame (inmem_store.go:136-150 -> GetRoot), a
@@ -313,6 +323,14 @@ void launch_block_json_write(const Dev &d, const Frames &fr, int32_t f0, int32_t
 // call that emits few frames)
 void launch_frame_store(const Dev &d, const Frames &fr, int32_t f0, int32_t F, const uint8_t *dig, hipStream_t s);
 void launch_block_store(const Dev &d, const Frames &fr, int32_t f0, int32_t F, const uint8_t *dig, hipStream_t s);
+// Sign hashes of frames [f0, f0 + F) from the Block JSON in bjson (as
+// launch_block_json_write left it): the body's span + '\n' hashed on the
+// device (-> shash), or the spans' digests `dig` computed elsewhere
+constexpr int64_t BLOCK_BODY_AT = 8;     // {"Body":
+constexpr int64_t BLOCK_BODY_TAIL = 18;  // ,"Signatures":{}}\n
+void launch_block_sign_hash(const Dev &d, const Frames &fr, int32_t f0, int32_t F, hipStream_t s);
+void launch_block_sign_store(const Dev &d, const Frames &fr, int32_t f0, int32_t F, const uint8_t *dig, hipStream_t s);
+void launch_block_bump_version(const Frames &fr, int32_t f0, int32_t F, hipStream_t s);
 // root (f, p) for every p: out[3p] NextRound, out[3p+1] SelfParent event (-1 base), out[3p+2] #Others
 void launch_root_query(const Dev &d, const Frames &fr, int32_t f, int32_t *out, hipStream_t s);
 
@@ -351,6 +369,43 @@ void launch_sha256(const uint8_t *data, const int64_t *off, const int32_t *len, 
                    hipStream_t s);  // kernels_sha.hip
 void launch_ecdsa_verify(const uint8_t *hash, const uint8_t *r, const uint8_t *s, const int32_t *key,
                          const uint8_t *pub, int64_t count, uint8_t *ok, hipStream_t st);  // kernels_ecdsa.hip
+// The block-signature pool on the device (kernels_sigpool.hip; sigpool.cpp):
+// ProcessSigPool (hashgraph.go:1236-1300).  Signature tables are indexed by
+// row = the block's frame, or R1 for the Reset block (which has no frame).
+struct SigPool {
+  int32_t n, R1, trust;          // trustCount = ceil(n / 3) (hashgraph.go:55)
+  int window;                    // the key tables' window width
+  const uint32_t *tab;           // fixed-key tables
+  // per (row, validator) and per row
+  uint8_t *set;                  // [(R1 + 1) n] a signature is stored
+  uint8_t *rs;                   // [(R1 + 1) n][64] r || s big-endian
+  int32_t *cnt;                  // [R1 + 1] len(block.Signatures)
+  int32_t *winner;               // [(R1 + 1) n] pass scratch: last valid pool position, -1
+  int64_t *misc;                 // [0] AnchorBlock + 1 (0 nil) [1] accepted [2] verified [3] survivors
+  // blocks held: block first_block + i is frame blk_rr[i]
+  const int32_t *blk_rr;
+  int64_t first_block, nblocks;
+  int64_t reset_block;           // -1 none; its sign hash (bh_set_reset_block_sign_hash) and version
+  const uint8_t *reset_shash;
+  int32_t reset_ver;             // -1: no sign hash installed
+  // the pool, in InsertEvent's append order (hashgraph.go:758), and the
+  // compaction's destination
+  int32_t *val, *val2;           // participant slot, -1 = not a participant
+  int64_t *blk, *blk2;           // BlockSignature.Index
+  uint8_t *prs, *prs2;           // [.][64] r || s
+  int32_t *seen, *seen2;         // version of the block at which the entry was judged invalid, -1 never
+  int32_t *row;                  // pass scratch: the entry's row, -1 = stays without a verdict
+  int8_t *stat;                  // pass scratch: 1 = valid
+};
+void launch_sig_pool_pass(const Frames &fr, const SigPool &sp, int64_t count, hipStream_t st);
+void launch_sig_set(const SigPool &sp, int32_t row, int32_t v, const uint8_t *rs, hipStream_t st);
+
+// fixed-key verification (kernels_sigpool.hip): windowed tables of the n
+// validators' keys and of G (window: 4 or 8 bits), and ecdsa.Verify through them
+size_t fixed_table_bytes(int32_t n, int window);
+void launch_fixed_tables(const uint8_t *pub, int32_t n, int window, uint32_t *tab, hipStream_t st);
+void launch_verify_fixed(const uint8_t *hash, const uint8_t *r, const uint8_t *s, const int32_t *val, int32_t n,
+                         int window, const uint32_t *tab, int64_t count, uint8_t *ok, hipStream_t st);
 void launch_flow_transpose(const Dev &d, hipStream_t s);
 // the chain dataflow for 128 < n <= 512 (kernels_flow_wide.hip): column-major
 // LA + LT rows; LA rows come from launch_flow_transpose, FD from kernels_fd

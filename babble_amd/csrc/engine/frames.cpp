@@ -102,6 +102,35 @@ int host_digests(bh_handle *h, const uint8_t *buf, const std::vector<int64_t> &o
   return BH_OK;
 }
 
+// sign digests (SHA-256 of BlockBody.Marshal(): the Block JSON's "Body"
+// value and a newline) of the F blocks host_digests just copied to
+// host_json, into the device buffer dig ([F][32])
+int host_sign_digests(bh_handle *h, const std::vector<int64_t> &ofs, int32_t F, uint8_t *dig) {
+  std::vector<uint8_t> out((size_t)F * 32);
+  auto work = [&](int32_t a, int32_t b) {
+    for (int32_t j = a; j < b; ++j) {
+      const int64_t len = ofs[(size_t)j + 1] - ofs[(size_t)j];
+      if (!len) continue;
+      uint8_t *p = h->host_json + ofs[(size_t)j];
+      uint8_t &sep = p[len - bh::BLOCK_BODY_TAIL];
+      sep = '\n';
+      SHA256(p + bh::BLOCK_BODY_AT, (size_t)(len - bh::BLOCK_BODY_AT - bh::BLOCK_BODY_TAIL + 1), out.data() + (size_t)j * 32);
+      sep = ',';
+    }
+  };
+  const int th = std::max(1, std::min<int>(HOST_SHA_THREADS, F));
+  if (th == 1) {
+    work(0, F);
+  } else {
+    std::vector<std::thread> ts;
+    for (int t = 0; t < th; ++t) ts.emplace_back(work, (int32_t)((int64_t)F * t / th), (int32_t)((int64_t)F * (t + 1) / th));
+    for (auto &t : ts) t.join();
+  }
+  HIPCHK(h, hipMemcpyAsync(dig, out.data(), out.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return BH_OK;
+}
+
 int read_offsets(bh_handle *h, const int64_t *src, int32_t F, std::vector<int64_t> *ofs) {
   ofs->resize((size_t)F + 1);
   HIPCHK(h, hipMemcpyAsync(ofs->data(), src, ((size_t)F + 1) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -142,6 +171,8 @@ int project_json(bh_handle *h, int32_t f0, int32_t F, int64_t i0, int64_t i1, bo
   if (bhost) {
     if (int rc = host_digests(h, fr.bjson, ofs, F, fr.dig)) return rc;
     bh::launch_block_store(d, fr, f0, F, fr.dig, s);
+    if (int rc = host_sign_digests(h, ofs, F, fr.sdig)) return rc;
+    bh::launch_block_sign_store(d, fr, f0, F, fr.sdig, s);
   }
   HIPCHK(h, hipStreamSynchronize(s));
   return BH_OK;
@@ -181,6 +212,8 @@ int frames_alloc_tables(bh_handle *h, bh::Frames &fr, int64_t R1, int64_t K, boo
   A(&fr.sz, S); A(&fr.sz2, S); A(&fr.part, S / 4096 + 2);
   A(&fr.missing, R1); A(&fr.jofs, R1 + 1); A(&fr.bofs, R1 + 1); A(&fr.jlen, R1); A(&fr.blen, R1);
   A(&fr.fhash, R1 * 32); A(&fr.bhash, R1 * 32); A(&fr.fvalid, R1); A(&fr.dig, R1 * 32);
+  A(&fr.shash, R1 * 32); A(&fr.st_len, R1); A(&fr.st_bytes, R1 * 64); A(&fr.bver, R1);
+  A(&fr.sofs, R1); A(&fr.slen, R1); A(&fr.sdig, R1 * 32);
   if (reset) {
     A(&fr.rsp_hash, n * 32); A(&fr.ro_key, K * 32); A(&fr.ro_hash, K * 32); A(&fr.ro_creator, K);
     A(&fr.ro_index, K); A(&fr.ro_lt, K); A(&fr.ro_round, K); A(&fr.ro_ofs, n + 1); A(&fr.ro_list, K);
@@ -195,7 +228,8 @@ void frames_free_tables(bh::Frames &fr) {
                   fr.last_pos, fr.first_pos, fr.last_in, fr.oofs, fr.okey, fr.oval, fr.ocur, fr.sz, fr.sz2,
                   fr.part, fr.missing, fr.jofs, fr.bofs, fr.jlen, fr.blen, fr.fhash, fr.bhash, fr.fvalid,
                   fr.dig, fr.json, fr.bjson, fr.rsp_hash, fr.ro_key, fr.ro_hash, fr.ro_creator, fr.ro_index,
-                  fr.ro_lt, fr.ro_round, fr.ro_ofs, fr.ro_list, fr.oth_of};
+                  fr.ro_lt, fr.ro_round, fr.ro_ofs, fr.ro_list, fr.oth_of, fr.shash, fr.st_len, fr.st_bytes,
+                  fr.bver, fr.sofs, fr.slen, fr.sdig};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   fr = bh::Frames{};
@@ -215,6 +249,9 @@ int frames_prepare(bh_handle *h, bh::Frames &fr, int64_t R1, size_t *json_cap, s
   HIPCHK(h, hipMemset(fr.fvalid, 0, (size_t)R1));
   HIPCHK(h, hipMemset(fr.fhash, 0, (size_t)R1 * 32));
   HIPCHK(h, hipMemset(fr.bhash, 0, (size_t)R1 * 32));
+  HIPCHK(h, hipMemset(fr.shash, 0, (size_t)R1 * 32));
+  HIPCHK(h, hipMemset(fr.st_len, 0xff, (size_t)R1 * 4));
+  HIPCHK(h, hipMemset(fr.bver, 0, (size_t)R1 * 4));
   const size_t cap = (1 << 20) + 128;
   *json_cap = *bjson_cap = 0;
   int rc;
@@ -258,6 +295,10 @@ void frames_reset(bh_handle *h) {
   (void)hipMemset(fr.fvalid, 0, (size_t)R1);
   (void)hipMemset(fr.fhash, 0, (size_t)R1 * 32);
   (void)hipMemset(fr.bhash, 0, (size_t)R1 * 32);
+  // the blocks are cut again: their StateHashes go with them
+  (void)hipMemset(fr.shash, 0, (size_t)R1 * 32);
+  (void)hipMemset(fr.st_len, 0xff, (size_t)R1 * 4);
+  (void)hipMemset(fr.bver, 0, (size_t)R1 * 4);
   h->others_total = 0;
 }
 
@@ -446,6 +487,78 @@ int64_t bh_get_block_json(bh_handle *h, int64_t b, int32_t body_only, uint8_t *b
     if (body_only && cap > len) buf[len] = '\n';
   }
   return out;
+}
+
+int bh_set_block_state_hashes(bh_handle *h, int64_t first, int64_t count, const uint8_t *bytes,
+                              const int64_t *offsets) {
+  if (!h) return BH_ERR_INVALID;
+  if (h->no_results()) return h->fail(BH_ERR_STATE, "results live on rank 0 of a split group");
+  if (!h->group.empty() || h->world > 1)
+    return h->fail(BH_ERR_STATE, "bh_set_block_state_hashes: one shard (block signatures are not sharded)");
+  if (!h->frames_on) return h->fail(BH_ERR_STATE, "bh_set_block_state_hashes: the handle was created without frames");
+  if (first < 0 || count < 0 || first + count > (int64_t)h->blocks.size())
+    return h->fail(BH_ERR_INVALID, "bh_set_block_state_hashes: blocks [%lld, %lld) out of range", (long long)first,
+                   (long long)(first + count));
+  if (count == 0) return BH_OK;
+  if (!offsets) return h->fail(BH_ERR_INVALID, "bh_set_block_state_hashes: null offsets");
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t l = offsets[i + 1] - offsets[i];
+    if (l < 0 || l > 64 || (l > 0 && !bytes))
+      return h->fail(BH_ERR_INVALID, "bh_set_block_state_hashes: block %lld: a StateHash has 0 to 64 bytes",
+                     (long long)(first + i));
+  }
+  (void)hipSetDevice(h->device);
+  hipStream_t s = h->stream;
+  HIPCHK(h, hipStreamSynchronize(s));
+  // blocks are in round-received order; a frame in between without events
+  // has no block and keeps no StateHash
+  const Block &b0 = h->blocks[(size_t)first], &b1 = h->blocks[(size_t)(first + count - 1)];
+  const int32_t r0 = b0.rr, F = b1.rr + 1 - r0;
+  std::vector<int32_t> len((size_t)F);
+  std::vector<uint8_t> val((size_t)F * 64);
+  HIPCHK(h, hipMemcpy(len.data(), h->fr.st_len + r0, (size_t)F * 4, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < count; ++i) {
+    const size_t f = (size_t)(h->blocks[(size_t)(first + i)].rr - r0);
+    len[f] = (int32_t)(offsets[i + 1] - offsets[i]);
+    if (len[f]) memcpy(val.data() + f * 64, bytes + offsets[i], (size_t)len[f]);
+  }
+  HIPCHK(h, hipMemcpyAsync(h->fr.st_len + r0, len.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->fr.st_bytes + (int64_t)r0 * 64, val.data(), (size_t)F * 64, hipMemcpyHostToDevice, s));
+  bh::launch_block_bump_version(h->fr, r0, F, s);
+  HIPCHK(h, hipGetLastError());
+  // the bodies again, with their StateHash, and their sign hashes; the
+  // block hash (bh_get_block_hashes: the hash as cut) stays
+  if (int rc = project_json(h, r0, F, b0.first, b1.first + b1.count, false, true)) return rc;
+  bh::launch_block_sign_hash(h->d, h->fr, r0, F, s);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(s));
+  return BH_OK;
+}
+
+int bh_get_block_sign_hashes(bh_handle *h, int64_t first, int64_t count, uint8_t *sign_hash, int8_t *valid) {
+  if (!h) return BH_ERR_INVALID;
+  if (h->no_results()) return h->fail(BH_ERR_STATE, "results live on rank 0 of a split group");
+  if (!h->frames_on) return h->fail(BH_ERR_STATE, "bh_get_block_sign_hashes: the handle was created without frames");
+  if (first < 0 || count < 0 || first + count > (int64_t)h->blocks.size())
+    return h->fail(BH_ERR_INVALID, "bh_get_block_sign_hashes: blocks [%lld, %lld) out of range", (long long)first,
+                   (long long)(first + count));
+  if (count == 0) return BH_OK;
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int32_t r0 = h->blocks[(size_t)first].rr, r1 = h->blocks[(size_t)(first + count - 1)].rr + 1;
+  std::vector<int8_t> ok((size_t)(r1 - r0));
+  std::vector<uint8_t> sh((size_t)(r1 - r0) * 32);
+  HIPCHK(h, hipMemcpy(ok.data(), h->fr.fvalid + r0, ok.size(), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(sh.data(), h->fr.shash + (int64_t)r0 * 32, sh.size(), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < count; ++i) {
+    const size_t f = (size_t)(h->blocks[(size_t)(first + i)].rr - r0);
+    if (valid) valid[i] = ok[f];
+    if (sign_hash) {
+      if (ok[f]) memcpy(sign_hash + 32 * i, sh.data() + 32 * f, 32);
+      else memset(sign_hash + 32 * i, 0, 32);
+    }
+  }
+  return BH_OK;
 }
 
 }  // extern "C"

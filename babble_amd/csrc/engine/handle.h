@@ -118,6 +118,22 @@ struct bh_handle {
   size_t pack_cap = 0;          // (int32 words)
   size_t q_cap = 0;
   size_t sha_cap = 0;
+  // fixed-key signature verification (bh_set_validators; sigpool.cpp)
+  uint32_t *sig_tab = nullptr;  // windowed tables of the validators' keys and of G (kernels_sigpool.hip)
+  int sig_window = 0;           // their window width in bits; 0 = no validators set
+  uint8_t *sig_buf = nullptr;   // bh_verify_fixed scratch
+  size_t sig_cap = 0;
+  hipEvent_t ev_sig[2]{};       // around the last verify / table / pool kernels (bh_get_sig_stats)
+  float verify_ms = 0, verify_fixed_ms = 0, tables_ms = 0, pool_ms = 0;
+  // the block-signature pool (sigpool.cpp), allocated by its first use
+  bh::SigPool sp{};
+  bool sp_on = false;
+  int64_t pool_count = 0, pool_cap = 0;
+  int32_t *sp_blk_rr = nullptr;  // [sp_blk_cap] frame of each held block; sp_blk_up uploaded
+  int64_t sp_blk_cap = 0, sp_blk_up = 0;
+  uint8_t *sp_reset_shash = nullptr;  // [32 + 64] the Reset block's sign hash, bh_set_block_signature staging
+  int32_t sp_reset_ver = -1;
+  int64_t sig_verified = 0, sig_accepted = 0, sig_verified_total = 0, sig_anchor = -1;
   hipEvent_t ev[NSTAGE + 1]{};
   hipEvent_t ev_sweep[2]{};  // around k_la_sweep alone (roofline timing)
   hipEvent_t ev_loop[2]{};
@@ -261,6 +277,11 @@ inline int dalloc(bh_handle *h, T **p, size_t count) {
   HIPCHK(h, hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
   return BH_OK;
 }
+
+// sigpool.cpp
+void sig_free(bh_handle *h);
+void sig_pool_forget(bh_handle *h);  // bh_reset_consensus: signatures, anchor and pool go with the blocks
+int sig_events(bh_handle *h);  // creates ev_sig on first use
 
 // frames.cpp
 int frames_alloc(bh_handle *h);

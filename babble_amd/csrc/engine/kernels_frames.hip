@@ -566,7 +566,15 @@ __device__ void block_head(JW &w, const Dev &d, const Frames &fr, int32_t f) {
   w.num(d.blk_of_frame[f]);
   w.lit(",\"RoundReceived\":");
   w.num(f);
-  w.lit(",\"StateHash\":null,\"FrameHash\":\"");
+  const int32_t sl = fr.st_len[f];  // Body.StateHash: nil until bh_set_block_state_hashes
+  if (sl < 0) {
+    w.lit(",\"StateHash\":null");
+  } else {
+    w.lit(",\"StateHash\":\"");
+    w.b64(fr.st_bytes + (int64_t)f * 64, sl);
+    w.lit("\"");
+  }
+  w.lit(",\"FrameHash\":\"");
   w.b64(fr.fhash + (int64_t)f * 32, 32);
   w.lit("\",\"Transactions\":[");
 }
@@ -640,7 +648,50 @@ void launch_block_json_write(const Dev &d, const Frames &fr, int32_t f0, int32_t
   if (store) {
     launch_sha256(fr.bjson, fr.bofs, fr.blen, F, fr.dig, s);
     launch_block_store(d, fr, f0, F, fr.dig, s);
+    launch_block_sign_hash(d, fr, f0, F, s);
   }
+}
+
+// BlockBody.Marshal() (block.go:21-29) is the Block JSON's "Body" value and
+// the Encoder's newline: {"Body":<body>,"Signatures":{}}\n.  The comma
+// behind the body becomes the newline while the span is hashed.
+__global__ __launch_bounds__(256) void k_sign_span(Frames fr, int32_t F, bool patch) {
+  const int32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= F) return;
+  const int64_t len = fr.blen[j];
+  if (patch) {
+    fr.sofs[j] = fr.bofs[j] + (len ? BLOCK_BODY_AT : 0);
+    fr.slen[j] = len ? (int32_t)(len - BLOCK_BODY_AT - BLOCK_BODY_TAIL + 1) : 0;
+  }
+  if (len) fr.bjson[fr.bofs[j] + len - BLOCK_BODY_TAIL] = patch ? '\n' : ',';
+}
+
+__global__ __launch_bounds__(256) void k_sign_store(Frames fr, int32_t f0, int32_t F, const uint8_t *h32) {
+  const int32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= F || fr.blen[j] == 0) return;
+  for (int k = 0; k < 32; ++k) fr.shash[(int64_t)(f0 + j) * 32 + k] = h32[(int64_t)j * 32 + k];
+}
+
+void launch_block_sign_store(const Dev &d, const Frames &fr, int32_t f0, int32_t F, const uint8_t *dig, hipStream_t s) {
+  if (F > 0) k_sign_store<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(fr, f0, F, dig);
+}
+
+void launch_block_sign_hash(const Dev &d, const Frames &fr, int32_t f0, int32_t F, hipStream_t s) {
+  if (F <= 0) return;
+  const unsigned g = (unsigned)((F + 255) / 256);
+  k_sign_span<<<g, 256, 0, s>>>(fr, F, true);
+  launch_sha256(fr.bjson, fr.sofs, fr.slen, F, fr.sdig, s);
+  k_sign_span<<<g, 256, 0, s>>>(fr, F, false);
+  launch_block_sign_store(d, fr, f0, F, fr.sdig, s);
+}
+
+__global__ __launch_bounds__(256) void k_bump_version(Frames fr, int32_t f0, int32_t F) {
+  const int32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j < F) fr.bver[f0 + j] += 1;
+}
+
+void launch_block_bump_version(const Frames &fr, int32_t f0, int32_t F, hipStream_t s) {
+  if (F > 0) k_bump_version<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(fr, f0, F);
 }
 
 void launch_block_store(const Dev &d, const Frames &fr, int32_t f0, int32_t F, const uint8_t *dig, hipStream_t s) {

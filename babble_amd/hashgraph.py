@@ -426,6 +426,27 @@ class Hashgraph:
         self._neg(self._L.bh_get_block_json(self._h, int(b), int(bool(body_only)), _ptr(buf), k))
         return buf[:k].tobytes()
 
+    def set_block_state_hashes(self, first, state_hashes):
+        """Body.StateHash of blocks first, first + 1, ... (node.go:619): a
+        sequence of bytes, 0 to 64 each.  The device rewrites the bodies with
+        the StateHash and rehashes them (bh_set_block_state_hashes)."""
+        lens = np.fromiter((len(b) for b in state_hashes), np.int64, len(state_hashes))
+        offsets = np.zeros(len(state_hashes) + 1, np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        data = np.frombuffer(b"".join(state_hashes) or b"\0", np.uint8)
+        self._check(self._L.bh_set_block_state_hashes(self._h, int(first), len(state_hashes), _ptr(data),
+                                                      _ptr(offsets)))
+
+    def block_sign_hashes(self, first=0, count=None):
+        """(sign_hash [m, 32], valid [m]) of blocks: BlockBody.Hash(), what
+        validators sign and Block.Verify checks (block.go:215-254)."""
+        st = self.stats()
+        count = st.blocks - st.first_block - first if count is None else count
+        sh = np.zeros((max(count, 1), 32), np.uint8)
+        ok = np.zeros(max(count, 1), np.int8)
+        self._check(self._L.bh_get_block_sign_hashes(self._h, int(first), int(count), _ptr(sh), _ptr(ok)))
+        return sh[:count], ok[:count].astype(bool)
+
     def hash_bodies(self, bodies):
         """Event.Hash() (event.go:50-56) of each body on the device: SHA-256
         of the Go-JSON bytes.  bodies: a sequence of bytes; returns [n, 32] u8."""
@@ -459,3 +480,104 @@ class Hashgraph:
         self._check(self._L.bh_verify_signatures(self._h, _ptr(hashes), _ptr(sig_r), _ptr(sig_s), _ptr(keys),
                                                  len(keys), _ptr(pubkeys), len(pubkeys), _ptr(out)))
         return out.astype(bool)
+
+    # ---- block signatures: the fixed signer set (block.go:234-254) ----
+    def set_validators(self, pubkeys):
+        """The participants' public keys in participant order, [n, 64] u8
+        (x || y big-endian; a leading 0x04 column is dropped): tabulates them
+        on the device for verify_fixed (bh_set_validators)."""
+        pubkeys = np.ascontiguousarray(pubkeys, np.uint8)
+        if pubkeys.ndim == 2 and pubkeys.shape[1] == 65:
+            pubkeys = np.ascontiguousarray(pubkeys[:, 1:])
+        if pubkeys.size != 64 * self.n:
+            raise ValueError("pubkeys must be [n, 64] bytes (x || y) in participant order")
+        self._check(self._L.bh_set_validators(self._h, _ptr(pubkeys)))
+
+    def verify_fixed(self, hashes, sig_r, sig_s, validators):
+        """Block.Verify (block.go:234-254) of a batch of signatures by the
+        handle's validators through their key tables: Go ecdsa.Verify
+        semantics.  hashes / sig_r / sig_s: [m, 32] u8 big-endian;
+        validators: [m] participant slots.  Returns [m] bool."""
+        validators = np.ascontiguousarray(validators, np.int32).reshape(-1)
+        m = len(validators)
+        hashes, sig_r, sig_s = (np.ascontiguousarray(a, np.uint8) for a in (hashes, sig_r, sig_s))
+        if any(a.size != 32 * m for a in (hashes, sig_r, sig_s)):
+            raise ValueError("hashes / sig_r / sig_s must hold 32 bytes per signature")
+        out = np.zeros(m, np.uint8)
+        self._check(self._L.bh_verify_fixed(self._h, _ptr(hashes), _ptr(sig_r), _ptr(sig_s), _ptr(validators),
+                                            m, _ptr(out)))
+        return out.astype(bool)
+
+    def verify_ms(self):
+        """Device times (ms) of the last verify_signatures / verify_fixed /
+        set_validators kernels, the tables' window width (bits) and size
+        (bytes), from bh_get_sig_stats."""
+        st = self.sig_stats()
+        return {"verify_signatures_ms": st.verify_signatures_ms, "verify_fixed_ms": st.verify_fixed_ms,
+                "set_validators_ms": st.set_validators_ms, "window_bits": st.window_bits,
+                "table_bytes": st.table_bytes}
+
+    def sig_stats(self):
+        st = _native.SigStats()
+        self._check(self._L.bh_get_sig_stats(self._h, C.byref(st)))
+        return st
+
+    # ---- the block-signature pool (ProcessSigPool, hashgraph.go:1236-1300) ----
+    def add_block_signatures(self, validators, block_index, sig_r, sig_s):
+        """InsertEvent's append to SigPool (hashgraph.go:758): validators [m]
+        participant slots (-1: not a participant), block_index [m], sig_r /
+        sig_s [m, 32] u8."""
+        validators = np.ascontiguousarray(validators, np.int32).reshape(-1)
+        block_index = np.ascontiguousarray(block_index, np.int64).reshape(-1)
+        m = len(validators)
+        sig_r, sig_s = (np.ascontiguousarray(a, np.uint8) for a in (sig_r, sig_s))
+        if len(block_index) != m or sig_r.size != 32 * m or sig_s.size != 32 * m:
+            raise ValueError("one block index and 32 bytes of r and s per signature")
+        self._check(self._L.bh_add_block_signatures(self._h, m, _ptr(validators), _ptr(block_index),
+                                                    _ptr(sig_r), _ptr(sig_s)))
+
+    def set_block_signature(self, block, validator, r, s):
+        """Block.SetSignature (core.go:152-161): no verification, no anchor move."""
+        r, s = (np.ascontiguousarray(a, np.uint8) for a in (r, s))
+        self._check(self._L.bh_set_block_signature(self._h, int(block), int(validator), _ptr(r), _ptr(s)))
+
+    def set_reset_block_sign_hash(self, hash32):
+        hash32 = np.ascontiguousarray(hash32, np.uint8)
+        self._check(self._L.bh_set_reset_block_sign_hash(self._h, _ptr(hash32)))
+
+    def process_sig_pool(self):
+        """ProcessSigPool: (accepted, remaining)."""
+        a, r = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.bh_process_sig_pool(self._h, C.byref(a), C.byref(r)))
+        return a.value, r.value
+
+    def block_signature_counts(self):
+        nb = self._neg(self._L.bh_get_block_signature_counts(self._h, 0, 0, None))
+        out = np.zeros(max(nb, 1), np.int32)
+        self._neg(self._L.bh_get_block_signature_counts(self._h, 0, nb, _ptr(out)))
+        return out[:nb]
+
+    def block_signatures(self, block):
+        """{slot: (r bytes, s bytes)} of block.Signatures."""
+        v = np.zeros(self.n, np.int32)
+        r = np.zeros((self.n, 32), np.uint8)
+        s = np.zeros((self.n, 32), np.uint8)
+        k = self._neg(self._L.bh_get_block_signatures(self._h, int(block), _ptr(v), _ptr(r), _ptr(s), self.n))
+        return {int(v[i]): (r[i].tobytes(), s[i].tobytes()) for i in range(k)}
+
+    @property
+    def anchor_block(self):
+        """Hashgraph.AnchorBlock: a block index or None."""
+        a = C.c_int64(0)
+        self._check(self._L.bh_get_anchor_block(self._h, C.byref(a)))
+        return None if a.value < 0 else a.value
+
+    def sig_pool(self):
+        """SigPool in order: [(slot, block index, r bytes, s bytes)]."""
+        m = self._neg(self._L.bh_get_sig_pool(self._h, None, None, None, None, 0))
+        v = np.zeros(max(m, 1), np.int32)
+        b = np.zeros(max(m, 1), np.int64)
+        r = np.zeros((max(m, 1), 32), np.uint8)
+        s = np.zeros((max(m, 1), 32), np.uint8)
+        self._neg(self._L.bh_get_sig_pool(self._h, _ptr(v), _ptr(b), _ptr(r), _ptr(s), m))
+        return [(int(v[i]), int(b[i]), r[i].tobytes(), s[i].tobytes()) for i in range(m)]

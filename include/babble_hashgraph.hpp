@@ -274,6 +274,84 @@ class Hashgraph {
     return GetRound(r).witnesses;
   }
 
+  // The participants' public keys (64 bytes each, x || y big-endian, in
+  // participant order), tabulated on the device for VerifyFixed
+  void SetValidators(const std::vector<uint8_t> &pubkeys) { check(bh_set_validators(h_, pubkeys.data())); }
+  // Block.Verify (block.go:234-254) of a batch of signatures by participants:
+  // 32 bytes of hash / r / s per signature, the signer's participant slot
+  std::vector<uint8_t> VerifyFixed(const std::vector<uint8_t> &hashes, const std::vector<uint8_t> &sig_r,
+                                   const std::vector<uint8_t> &sig_s, const std::vector<int32_t> &validator) const {
+    std::vector<uint8_t> ok(validator.size());
+    check(bh_verify_fixed(h_, hashes.data(), sig_r.data(), sig_s.data(), validator.data(),
+                          (int64_t)validator.size(), ok.data()));
+    return ok;
+  }
+
+  // Body.StateHash of blocks first, first + 1, ... (node.go:619; 0 to 64
+  // bytes each): the device rewrites and rehashes their bodies
+  void SetBlockStateHashes(int64_t first, const std::vector<std::vector<uint8_t>> &state_hashes) {
+    std::vector<int64_t> off(state_hashes.size() + 1, 0);
+    std::vector<uint8_t> flat(1, 0);
+    for (size_t i = 0; i < state_hashes.size(); ++i) {
+      flat.insert(flat.end(), state_hashes[i].begin(), state_hashes[i].end());
+      off[i + 1] = off[i] + (int64_t)state_hashes[i].size();
+    }
+    check(bh_set_block_state_hashes(h_, first, (int64_t)state_hashes.size(), flat.data() + 1, off.data()));
+  }
+  // BlockBody.Hash() of blocks [first, first + count): what validators sign
+  // (block.go:215-254), 32 bytes each
+  std::vector<uint8_t> BlockSignHashes(int64_t first, int64_t count) const {
+    std::vector<uint8_t> out((size_t)count * 32 + 1);
+    check(bh_get_block_sign_hashes(h_, first, count, out.data(), nullptr));
+    out.resize((size_t)count * 32);
+    return out;
+  }
+
+  // InsertEvent's append of an event's BlockSignatures to SigPool
+  // (hashgraph.go:758): participant slots (-1: not a participant), block
+  // indexes, 32 bytes of r and of s per signature
+  void AddBlockSignatures(const std::vector<int32_t> &validator, const std::vector<int64_t> &block_index,
+                          const std::vector<uint8_t> &sig_r, const std::vector<uint8_t> &sig_s) {
+    check(bh_add_block_signatures(h_, (int64_t)validator.size(), validator.data(), block_index.data(), sig_r.data(),
+                                  sig_s.data()));
+  }
+  // Block.SetSignature as Core.SignBlock uses it (core.go:152-161)
+  void SetBlockSignature(int64_t block, int32_t validator, const uint8_t *r, const uint8_t *s) {
+    check(bh_set_block_signature(h_, block, validator, r, s));
+  }
+  void SetResetBlockSignHash(const uint8_t *hash32) { check(bh_set_reset_block_sign_hash(h_, hash32)); }
+  // ProcessSigPool (hashgraph.go:1236-1300): {accepted, remaining}
+  std::pair<int64_t, int64_t> ProcessSigPool() {
+    int64_t a = 0, r = 0;
+    check(bh_process_sig_pool(h_, &a, &r));
+    return {a, r};
+  }
+  // Hashgraph.AnchorBlock (nil: nullopt)
+  std::optional<int64_t> AnchorBlock() const {
+    int64_t a = -1;
+    check(bh_get_anchor_block(h_, &a));
+    if (a < 0) return std::nullopt;
+    return a;
+  }
+  // len(block.Signatures) of every block the engine cut
+  std::vector<int32_t> BlockSignatureCounts() const {
+    const int64_t nb = bh_get_block_signature_counts(h_, 0, 0, nullptr);
+    if (nb < 0) check((int)-nb);
+    std::vector<int32_t> c((size_t)std::max<int64_t>(nb, 0));
+    if (nb > 0) bh_get_block_signature_counts(h_, 0, nb, c.data());
+    return c;
+  }
+  int64_t SigPoolSize() const {
+    const int64_t m = bh_get_sig_pool(h_, nullptr, nullptr, nullptr, nullptr, 0);
+    if (m < 0) check((int)-m);
+    return m;
+  }
+  bh_sig_stats SigStats() const {
+    bh_sig_stats s{};
+    check(bh_get_sig_stats(h_, &s));
+    return s;
+  }
+
   // lastAncestors / firstDescendants indexes of one event (event.go:115-116),
   // in participant order; -1 / INT32_MAX as in the reference
   std::pair<std::vector<int32_t>, std::vector<int32_t>> Coordinates(int64_t id, int n) const {

@@ -254,6 +254,104 @@ int bh_verify_signatures(bh_handle *h, const uint8_t *hashes, const uint8_t *sig
                          const int32_t *keys, int64_t count, const uint8_t *pubkeys, int32_t n_keys,
                          uint8_t *ok);
 
+/* ---- Block signatures: the fixed signer set ----
+ * Every validator signs every block and gossips the signature on its next
+ * event (node.go:605-630); ProcessSigPool (hashgraph.go:1236-1300) and
+ * CheckBlock (hashgraph.go:1483-1497) verify them with Block.Verify
+ * (block.go:234-254).  The signers are the handle's n participants, so
+ * their keys are tabulated once.
+ *
+ * bh_set_validators: pubkeys holds the n participants' public keys in
+ * participant (peer) order, 64 bytes each: x || y big-endian.  A key that
+ * is not a point of P-256 fails with BH_ERR_INVALID and leaves the handle as
+ * it was.  A device kernel builds, per validator and for the generator G,
+ * a table of the multiples d 2^(8j) P (d in [1, 255], j in [0, 32)) in
+ * affine Montgomery form: 522,240 bytes per validator (BH_SIG_WINDOW=4 in
+ * the environment: 4-bit windows, 61,440 bytes, about 0.6x the rate).  May be called again
+ * (a new peer set's keys); synchronous.  BH_ERR_STATE on a sharded handle
+ * (bh_config.n_devices > 1 or bh_comm_init*): block signatures are not
+ * sharded. */
+int bh_set_validators(bh_handle *h, const uint8_t *pubkeys);
+/* Go ecdsa.Verify(pub, hash, r, s), as bh_verify_signatures runs it, of a
+ * batch of signatures by the handle's validators: signature i (32-byte
+ * big-endian hash / r / s at 32 * i) by the participant in slot
+ * validator[i] in [0, n).  u1 G + u2 Q is a sum of table entries (no
+ * doublings), one thread per signature; ok[i] = 1 if it verifies, else 0.
+ * CheckBlock's loop over a block's participant signatures is this call with
+ * one hash repeated; signatures by keys outside the participant set stay on
+ * bh_verify_signatures.  BH_ERR_STATE before bh_set_validators and on a
+ * sharded handle.  Synchronous, on the handle's stream. */
+int bh_verify_fixed(bh_handle *h, const uint8_t *hashes, const uint8_t *sig_r, const uint8_t *sig_s,
+                    const int32_t *validator, int64_t count, uint8_t *ok);
+
+/* ---- Block signatures: the pool (ProcessSigPool, hashgraph.go:1236-1300) ----
+ * Needs bh_config.frames (the sign hashes) and bh_set_validators; a sharded
+ * handle returns BH_ERR_STATE (block signatures are not sharded).  Blocks
+ * are named by Block.Index().  The pool, the stored signatures and
+ * AnchorBlock live on the device.
+ *
+ * bh_add_block_signatures: InsertEvent's append of the event's
+ * BlockSignatures to SigPool (hashgraph.go:758), in order.  validator[i] is
+ * the signer's participant slot, or -1 for a key outside the participant
+ * set; sig_r / sig_s are the decoded signature, 32 bytes big-endian each.
+ * The pool grows as needed. */
+int bh_add_block_signatures(bh_handle *h, int64_t count, const int32_t *validator, const int64_t *block_index,
+                            const uint8_t *sig_r, const uint8_t *sig_s);
+/* Block.SetSignature as Core.SignBlock uses it (core.go:152-161,
+ * block.go:234-237): stores the signature for (block, validator) without
+ * verifying it and without moving the anchor.  BH_ERR_KEY_NOT_FOUND for a
+ * block the handle does not hold. */
+int bh_set_block_signature(bh_handle *h, int64_t block, int32_t validator, const uint8_t *r, const uint8_t *s);
+/* The Reset block (bh_reset's block_index) is stored without a body, so the
+ * caller installs its sign hash (block.Body.Hash()); pooled signatures for
+ * that index then resolve as in Go, where Store.GetBlock returns the Reset
+ * block.  BH_ERR_STATE on a handle without a Reset block. */
+int bh_set_reset_block_sign_hash(bh_handle *h, const uint8_t *hash32);
+/* ProcessSigPool: device work on the handle's stream and one read-back, no
+ * host loop over signatures.  Per pooled entry, with the results of the
+ * reference's sequential loop: unknown validator (-1), block not held (not
+ * cut yet, below first_block and not the Reset block, or its bytes
+ * incomplete) and invalid against the block's current sign hash all stay
+ * pooled, in order; a valid signature is stored for (block, validator) and
+ * leaves the pool (a later valid entry for the same pair replaces an earlier
+ * one, the count stays 1).  AnchorBlock becomes the highest block that
+ * accepted a signature in this call and now holds more than trustCount =
+ * ceil(n / 3) signatures, if above the old one.  An entry judged invalid is
+ * not verified again until its block's body changes
+ * (bh_set_block_state_hashes).  accepted: entries that left the pool;
+ * remaining: the pool's size after the call.  Pointers nullable. */
+int bh_process_sig_pool(bh_handle *h, int64_t *accepted, int64_t *remaining);
+/* len(block.Signatures) of the blocks [first, first + count) the engine cut
+ * (numbered as in bh_get_block_hashes) into counts (nullable); returns the
+ * number of blocks or a negative status. */
+int64_t bh_get_block_signature_counts(bh_handle *h, int64_t first, int64_t count, int32_t *counts);
+/* block.Signatures of block `block` (Block.Index(); the Reset block
+ * included) by ascending participant slot: up to cap entries into
+ * validators / r / s (nullable); returns their number or a negative status. */
+int32_t bh_get_block_signatures(bh_handle *h, int64_t block, int32_t *validators, uint8_t *r, uint8_t *s,
+                                int32_t cap);
+/* Hashgraph.AnchorBlock (hashgraph.go:1302-1321): the block's Index, -1 for
+ * nil.  bh_reset leaves it nil (hashgraph.go:1329); bh_reset_consensus
+ * forgets block signatures, StateHashes, the anchor and the pool (the blocks
+ * are cut again; the caller adds the signatures again). */
+int bh_get_anchor_block(bh_handle *h, int64_t *index);
+/* SigPool in order: up to cap entries (arrays nullable); returns the pool's
+ * size or a negative status. */
+int64_t bh_get_sig_pool(bh_handle *h, int32_t *validator, int64_t *block_index, uint8_t *sig_r, uint8_t *sig_s,
+                        int64_t cap);
+/* engine introspection (no reference counterpart): the pool's size; the
+ * signatures the last bh_process_sig_pool verified and accepted; all it
+ * verified so far; the key tables' bytes and window width; trustCount; the
+ * device time (ms) of the kernels of the last bh_verify_signatures (on a
+ * handle with validators), bh_verify_fixed, bh_set_validators and
+ * bh_process_sig_pool */
+typedef struct bh_sig_stats {
+  int64_t pool, verified, accepted, verified_total, table_bytes;
+  int32_t window_bits, trust_count;
+  float verify_signatures_ms, verify_fixed_ms, set_validators_ms, process_sig_pool_ms;
+} bh_sig_stats;
+int bh_get_sig_stats(bh_handle *h, bh_sig_stats *out);
+
 /* ---- Block projection (bh_config.frames) ----
  * The bytes Frame.Marshal (frame.go:17-26) needs of events [first, first +
  * count) (already inserted): body i = bodies[body_offsets[i] ..
@@ -291,6 +389,28 @@ int bh_get_block_hashes(bh_handle *h, int64_t first, int64_t count, uint8_t *fra
  * block.go:21-29 -- what checkGossip compares) of block b: length, up to
  * cap bytes copied; negative status when unavailable. */
 int64_t bh_get_block_json(bh_handle *h, int64_t b, int32_t body_only, uint8_t *buf, int64_t cap);
+/* Body.StateHash of blocks [first, first + count) (numbered as in
+ * bh_get_block_hashes), as the app's CommitBlock returns it and the node
+ * stores it (node.go:619-626): block first + i gets bytes[offsets[i] ..
+ * offsets[i+1]) (offsets: count + 1 ascending entries; 0 to 64 bytes each,
+ * longer is BH_ERR_INVALID and changes nothing).  On the device the bodies
+ * are written again with "StateHash":"<base64>" and rehashed, and each
+ * block's version is bumped.  bh_get_block_json then shows the StateHash in
+ * both forms ("Signatures":{} stays empty) and bh_get_block_sign_hashes the
+ * new sign hash; bh_get_block_hashes keeps its meaning, the hash as cut.
+ * bh_reset_consensus forgets StateHashes (the blocks are cut again).
+ * BH_ERR_STATE without bh_config.frames and on a sharded handle. */
+int bh_set_block_state_hashes(bh_handle *h, int64_t first, int64_t count, const uint8_t *bytes,
+                              const int64_t *offsets);
+/* What validators sign and Block.Verify checks (block.go:215-254): the sign
+ * hash BlockBody.Hash() = SHA-256 of BlockBody.Marshal() (block.go:21-46)
+ * of blocks [first, first + count), 32 bytes each, with the StateHash the
+ * block has now.  Every ProcessDecidedRounds that stores a block hash stores
+ * the sign hash in the same projection.  valid[i] = 0 when the frame's
+ * bytes were incomplete (the hash is then zero).  Arrays nullable.
+ * CheckBlock for participant signers is bh_verify_fixed with this hash
+ * repeated. */
+int bh_get_block_sign_hashes(bh_handle *h, int64_t first, int64_t count, uint8_t *sign_hash, int8_t *valid);
 
 /* Sharding across processes: one shard per process,
  * each holding the whole DAG, joined by an RCCL communicator.  Rank 0 makes
