@@ -7,7 +7,7 @@ CC ?= gcc
 ENGINE_SRC := $(wildcard babble_amd/csrc/engine/*.hip) $(wildcard babble_amd/csrc/engine/*.cpp)
 ENGINE_HDR := $(wildcard babble_amd/csrc/engine/*.h) include/babble_hip.h
 
-all: babble_amd/libbabble_gen.so babble_amd/libbabble_hip.so oracle/liboracle.so tests/cpp/hg_replay
+all: babble_amd/libbabble_gen.so babble_amd/libbabble_hip.so oracle/liboracle.so tests/cpp/hg_replay tests/cpp/sched_plan_check
 
 babble_amd/libbabble_gen.so: babble_amd/csrc/dag_gen.c babble_amd/csrc/dag_gen.h
 	$(CC) -O2 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
@@ -29,8 +29,12 @@ oracle/liboracle.so: oracle/hg_oracle.c oracle/hg_oracle.h
 tests/cpp/hg_replay: tests/cpp/hg_replay.cpp include/babble_hashgraph.hpp include/babble_hip.h babble_amd/libbabble_hip.so
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ $< -Lbabble_amd -lbabble_hip -Wl,-rpath,'$$ORIGIN/../../babble_amd'
 
+# host check of the scheduling arithmetic (plain g++: no device, no engine library)
+tests/cpp/sched_plan_check: tests/cpp/sched_plan_check.cpp babble_amd/csrc/engine/sched_plan.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -o $@ $<
+
 # host-only AddressSanitizer build of the engine (tools/sanitize_engine.sh):
-# the host files (api.cpp, frames.cpp) built by g++ with -fsanitize=address
+# the host files (api.cpp, rounds.cpp, split.cpp, frames.cpp, ...) built by g++ with -fsanitize=address
 # and UBSan, linked with the regular gfx950 kernel objects, loaded through
 # BH_LIB_PATH with GCC's ASan runtime preloaded.  (clang's ROCm ASan runtime
 # intercepts hsa_amd_memory_pool_allocate for device-side ASan, which needs
@@ -48,6 +52,6 @@ tools/asan/libbabble_hip.so: $(ASAN_OBJ) $(KERNEL_OBJ)
 asan: tools/asan/libbabble_hip.so
 
 clean:
-	rm -rf babble_amd/*.so oracle/*.so tests/cpp/hg_replay build/engine build/asan tools/asan
+	rm -rf babble_amd/*.so oracle/*.so tests/cpp/hg_replay tests/cpp/sched_plan_check build/engine build/asan tools/asan
 
 .PHONY: all asan clean

@@ -150,7 +150,7 @@ struct Dev {
   int32_t use_cla;  // the loop that ran wrote cla (k_round2; not the resident k_round_solo)
   int32_t wide_cols;  // the 16-bit wide loop reads la_col (k_round_wide<*, true, true>; no FDT)
   int32_t round_persist;  // k_round2p: the whole n <= 128 loop in one launch (default; BH_ROUND_PERSIST=0: one launch per iteration)
-  int32_t round_f32;      // k_round2p's search compares in packed f32 (BH_ROUND_F32=0: the int32 sign-bit count)
+  int32_t round_f32;      // BH_ROUND_F32=1 (default): k_round_lean; 0, or chains >= 2^22 - 2 rows: the int32 k_round2p
   int32_t cand_fe;        // candfd rows in k_round_lean's float encoding (set by the launchers, cand_fe())
   int32_t *pbar;          // the persistent wide loop's grid barrier (k_round2p hands off through tagged Bp / candfd dwords instead)
   int32_t pbar_spin;      // polls before a persistent loop gives up waiting (barrier or tagged hand-off; BH_PBAR_SPIN lowers it to test the fallback)

@@ -1,13 +1,16 @@
 // handle.h -- host state of a libbabble_hip handle (internal; shared by
-// api.cpp, the passes and queries, and frames.cpp, the block projection).
+// api.cpp, the C ABI, passes and queries; rounds.cpp and split.cpp,
+// DivideRounds' scheduling; frames.cpp, the block projection; sigpool.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -136,9 +139,9 @@ struct bh_handle {
   int64_t sig_verified = 0, sig_accepted = 0, sig_verified_total = 0, sig_anchor = -1;
   hipEvent_t ev[NSTAGE + 1]{};
   hipEvent_t ev_sweep[2]{};  // around k_la_sweep alone (roofline timing)
-  hipEvent_t ev_loop[2]{};
-  hipEvent_t ev_st = nullptr;  // behind the loop state's read-back (rounds_pipelined: the witness tables run after it)
-  bool fuse_fame = false;      // bh_run_consensus: DecideFame follows DivideRounds at once (rounds_tail)   // around each round loop (run_round_loop): its device time, summed per run
+  hipEvent_t ev_loop[2]{};   // around each round loop (run_round_loop): its device time, summed per run
+  hipEvent_t ev_st = nullptr;  // behind the loop state's read-back (SegmentPipeline: the witness tables run after it)
+  bool fuse_fame = false;      // bh_run_consensus: DecideFame follows DivideRounds at once (rounds_tail)
   float loop_ms = 0, loop_ms_acc = 0;
   float sweep_ms = 0;
   const char *sweep_kernel = "";
@@ -297,3 +300,176 @@ void frames_reset(bh_handle *h);
 // roots, FrameHash and block hashes of the frames [P0, P1) just processed
 // (consensus positions [i0, i1))
 int frames_project(bh_handle *h, int32_t P0, int32_t P1, int64_t i0, int64_t i1);
+
+// api.cpp: host helpers the passes share
+int upload(bh_handle *h);  // events inserted since the last upload
+hipError_t wait_stream(hipStream_t s);
+hipError_t copy_sync(hipStream_t s, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+int rd_async(bh_handle *h, hipStream_t s, void *dst, const void *src, size_t bytes);
+int rd_wait(bh_handle *h, hipStream_t s);
+int rd_wait_event(bh_handle *h, hipEvent_t e);
+void settle_timings(bh_handle *h);
+std::vector<size_t> range_bytes(const bh_handle *h, int64_t items, size_t esz, bool lengths,
+                                const std::vector<int32_t> *ofs = nullptr, int64_t base = 0);
+
+// shards: ranges, local execution, exchanges
+
+// [lo, hi) of `items` owned by shard `rank` of `world`: contiguous, sizes
+// differ by at most one (bh_shard_range exposes it to the tests)
+inline void shard_range(int64_t items, int32_t world, int32_t rank, int64_t *lo, int64_t *hi) {
+  *lo = items * rank / world;
+  *hi = items * (rank + 1) / world;
+}
+
+// the shards this process drives for handle h
+inline std::vector<bh_handle *> local_shards(bh_handle *h) {
+  return h->group.empty() ? std::vector<bh_handle *>{h} : h->group;
+}
+
+// run fn on every local shard: one host thread per shard of an in-process
+// group (each on its own device and stream; the round loop polls its device
+// from the host), inline otherwise.  The first failure is reported on h.
+template <class F>
+int run_local(bh_handle *h, F fn) {
+  if (h->group.size() <= 1) return fn(h);
+  const size_t G = h->group.size();
+  std::vector<int> rc(G, BH_OK);
+  std::vector<std::thread> th;
+  for (size_t i = 0; i < G; ++i)
+    th.emplace_back([&, i] {
+      bh_handle *s = h->group[i];
+      if (hipSetDevice(s->device) != hipSuccess) { rc[i] = s->fail(BH_ERR_DEVICE, "hipSetDevice"); return; }
+      rc[i] = fn(s);
+    });
+  for (auto &t : th) t.join();
+  for (size_t i = 0; i < G; ++i)
+    if (rc[i] != BH_OK) {
+      if (h->group[i] != h) h->err = "shard " + std::to_string(i) + ": " + h->group[i]->err;
+      (void)hipSetDevice(h->device);
+      return rc[i];
+    }
+  (void)hipSetDevice(h->device);
+  return BH_OK;
+}
+
+// All-gather of per-shard byte ranges of one device buffer (same layout on
+// every shard): shard r owns [off[r], off[r] + len[r]) of the buffer `sel`
+// selects; afterwards every shard holds every range.  In-process: each
+// shard's stream waits for the owner's work, then peer-copies the range
+// (xGMI between devices, a device copy on a shared one).  Across processes:
+// one ncclBroadcast per owner, in place, grouped.
+template <class Sel>
+int exchange(bh_handle *h, Sel sel, const std::vector<size_t> &off, const std::vector<size_t> &len) {
+  if (h->world <= 1) return BH_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (h->xport) {
+    uint8_t *base = reinterpret_cast<uint8_t *>(sel(h));
+    int rc;
+    if ((rc = h->xport->group_start(h))) return rc;
+    for (int r = 0; r < h->world; ++r)
+      if (len[r] && (rc = h->xport->bcast(h, base + off[r], len[r], r, h->stream))) {
+        (void)h->xport->group_end(h);
+        return rc;
+      }
+    if ((rc = h->xport->group_end(h))) return rc;
+    HIPCHK(h, wait_stream(h->stream));
+  } else {
+    const size_t G = h->group.size();
+    std::vector<hipEvent_t> ready(G);
+    for (size_t r = 0; r < G; ++r) {
+      bh_handle *o = h->group[r];
+      HIPCHK(h, hipSetDevice(o->device));
+      HIPCHK(h, hipEventCreateWithFlags(&ready[r], hipEventDisableTiming));
+      HIPCHK(h, hipEventRecord(ready[r], o->stream));
+    }
+    for (size_t t = 0; t < G; ++t) {
+      bh_handle *dst = h->group[t];
+      HIPCHK(h, hipSetDevice(dst->device));
+      uint8_t *db = reinterpret_cast<uint8_t *>(sel(dst));
+      for (size_t r = 0; r < G; ++r) {
+        if (r == t || !len[r]) continue;
+        bh_handle *src = h->group[r];
+        HIPCHK(h, hipStreamWaitEvent(dst->stream, ready[r], 0));
+        HIPCHK(h, hipMemcpyPeerAsync(db + off[r], dst->device, reinterpret_cast<uint8_t *>(sel(src)) + off[r],
+                                     src->device, len[r], dst->stream));
+      }
+    }
+    for (size_t t = 0; t < G; ++t) {
+      HIPCHK(h, hipSetDevice(h->group[t]->device));
+      HIPCHK(h, wait_stream(h->group[t]->stream));
+      (void)hipEventDestroy(ready[t]);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+  }
+  h->xchg_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return BH_OK;
+}
+
+// rounds.cpp: DivideRounds' host scheduling
+int stage_rounds(bh_handle *h);
+int set_chain_tables(bh_handle *h, bool wait = true);
+bool use_flow(const Dev &d);
+int ensure_fd(bh_handle *h);
+int reset_coords(bh_handle *h, hipStream_t s);
+int build_rows(bh_handle *h, const std::vector<int32_t> &upto, hipStream_t s);
+int rounds_coords(bh_handle *h);
+int rounds_loop(bh_handle *h);
+int rounds_segmented(bh_handle *h, bool *used);
+int segments_for(const Dev &d, int64_t events);
+double seg_ratio(const Dev &d);
+void chain_lens_at(const bh_handle *h, int64_t bound, int32_t *out);
+// events of the current layout an incremental call keeps (0: a full call)
+inline int64_t resume_base(const bh_handle *h, int64_t N) {
+  return (!h->layout_changed && h->inc_valid && N >= h->n_coord) ? h->n_coord : 0;
+}
+// the resume bookkeeping after a call's coordinates: the device holds those
+// of the first N events of the current layout (lens_h their chain lengths);
+// valid: the next call may resume from them (else rounds_tail's LT fallback
+// overwrote FDT and dropped coords_for)
+inline void commit_coords(bh_handle *h, int64_t N, bool valid) {
+  if (valid) h->coords_for = (int)N;
+  h->n_coord = N;
+  h->lens_coord = h->lens_h;
+  h->inc_valid = valid;
+}
+// segment k of a call cut at Ns: events [Ns[k], Ns[k + 1]), its chain ranges
+// [lo | len][n] at lens (device)
+inline Dev segment_view(const bh_handle *h, const Dev &d, int32_t *lens, const int64_t *Ns, int k) {
+  Dev v = d;
+  v.seg_lo = lens;
+  v.chain_len = lens + d.n;
+  v.N = Ns[k + 1];
+  v.e0 = Ns[k];
+  v.rows = h->layout_rows;
+  return v;
+}
+int ensure_events(bh_handle *h, std::vector<hipEvent_t> &v, size_t count, unsigned flags);  // grow v to count events
+
+// split.cpp: the coordinate split.  One call's segments, alike on every
+// shard: boundaries, each segment's chain ranges [lo, hi) and packing tables
+// P (rows before chain c) and Q (64-row chunks before chain c), the blocks'
+// sizes
+struct SplitPlan {
+  int K = 0;
+  int64_t base = 0;
+  std::vector<int64_t> Ns, S, NQ;
+  std::vector<int32_t> tab;  // [K][lo, hi][n], then [K][P, Q][n + 1]
+  // block (k, r) at byte offset off[k * world + r] of every shard's xbuf
+  // (segment-major, then coordinate rank): one layout everywhere, so a
+  // block is broadcast in place and peer-copied offset to offset
+  std::vector<size_t> off;
+  size_t total = 0;
+  size_t boff(const bh_handle *h, int k, int32_t rank) const { return off[(size_t)k * h->world + rank]; }
+  int32_t *dview(const bh_handle *h, int k) const { return h->xseg + (size_t)k * 2 * h->d.n; }
+  const int32_t *dpq(const bh_handle *h, int k) const {
+    return h->xseg + (size_t)K * 2 * h->d.n + (size_t)k * 2 * (h->d.n + 1);
+  }
+  size_t block_bytes(const bh_handle *h, int k, int32_t rank) const;
+  bh::SplitBlock block(const bh_handle *h, int k, int32_t rank, uint8_t *at) const;
+};
+int split_prepare(bh_handle *x, const SplitPlan &p, size_t bytes);
+int rounds_split_stage(bh_handle *h);
+// the segment pipeline (rounds.cpp) over K segments from base; sp / grp: the
+// split's plan and in-process group
+int rounds_pipelined(bh_handle *h, int K, int64_t base, const SplitPlan *sp = nullptr,
+                     const std::vector<bh_handle *> *grp = nullptr);

@@ -12,8 +12,9 @@ test_gpu_shard.py, test_gpu_comm.py).
   the kernels (realtime stamps, counters) and the segment pipeline waiting
   for every segment's loop;
 * BH_LOOP_TIMING=0 -- no HIP events around the loop (stage 7 reads 0);
-* BH_ROUND_F32=0 -- k_round2p's search counting in int32 (sign bits of
-  LA - FD) instead of packed f32 with the clamp modifier (the default);
+* BH_ROUND_F32=0 -- the int32 k_round2p (its search counts sign bits of
+  LA - FD; chains of at least 2^22 - 2 rows take it too) instead of
+  k_round_lean, packed f32 with the clamp modifier (=1, the default);
 * BH_SEG_RATIO -- the segment pipeline's growth ratio (segment k holds a
   ratio^k share of the events): equal segments (1.0) and steep ones (1.8)
   cut the DAG at other boundaries than the defaults (1.15 above n = 96).
